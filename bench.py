@@ -5,19 +5,30 @@ One "step" = one generate() over the per-GPU batch: RCCL broadcast of the text e
 from rank 0, 50 graph-replayed denoising steps (UNet on the CFG batch 2B, CFG combine, DDIM),
 gather of the final latents.  Weak scaling: every rank denoises B=4 prompts per step.
 
-Also reported (rank 0):
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed steps,
+the optional --dump-outputs, the result line (with the figures that are arithmetic on the timed
+value: path_roofline, int8_blended_roofline, the kernel families the loop's linears ran).
+
+Reported in addition with --full (rank 0; each is a measurement of its own after the timed steps):
   roofline      the dominant kernel (the largest conv implicit GEMM of the UNet) timed live
                 with HIP events on the stream it runs on; ALGORITHMIC flops / duration vs the
                 fp16 dense MFMA peak (the path computes fake-quant operands in fp16)
-  path_roofline whole-loop FLOP rate (803.3 GFLOP per UNet eval per sample, SURVEY App. B)
   cpu_baseline  BASELINE.md §2: the reference's CPU path (config C1) restated by the oracle
                 (torch-CPU fp16 ops) timed on this box's host cores: every distinct op shape of a
                 UNet evaluation on a bounded slice, warm-up + median of 3 (see cpu_baseline())
+  end_to_end    text encoder + VAE decode around the timed loop
+  int8_mode     the same workload in the int8-MFMA mode (a second model, its own timed steps)
+Every run:
+  path_roofline whole-loop FLOP rate (803.3 GFLOP per UNet eval per sample, SURVEY App. B)
   int8_blended_roofline  images/s against the int8-MFMA-blended bound of north_star's target
 Secondary lines (same JSON contract): --model sdxl (SURVEY config C4: SDXL W8A8 1024^2, 2
 prompts per GPU, 50 EulerDiscrete steps) and --model sd35 (config C5: SD3.5-Large W4A16 g128
 1024^2, 1 prompt per GPU, flow-match Euler).
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--model sd15|sdxl|sd35]
+--dump-outputs DIR writes what the last timed step returned (the gathered final latents, rank 0)
+as DIR/latents.npy in float32; weights, text embeddings and initial latents are seeded, and the
+committed GEMM table fixes every kernel choice, so two builds can be compared output for output.
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--model sd15|sdxl|sd35] [--full]
+                       [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -55,8 +66,14 @@ def parse():
     ap.add_argument("--calib-steps", type=int, default=50)
     ap.add_argument("--calib-samples", type=int, default=96)
     ap.add_argument("--calib-batch", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the text encoder + VAE end-to-end timing")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the dominant kernel's roofline, the end-to-end "
+                         "(text encoder + VAE) time, the int8-MFMA mode object and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true",
+                    help="with --full: skip the text encoder + VAE end-to-end timing")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0: every usable core (sched_getaffinity, capped by the cgroup CPU quota)")
     ap.add_argument("--epi-lds", action="store_true",
@@ -64,7 +81,7 @@ def parse():
     ap.add_argument("--gn-geom", default=None,
                     help="measurement: GroupNorm statistics / apply rows per thread 'S,A' (qd_gn_geom_force, A/B runs)")
     ap.add_argument("--no-int8-mode", action="store_true",
-                    help="skip the int8-MFMA mode object of the default SD1.5 W8A8 line")
+                    help="with --full: skip the int8-MFMA mode object of the default SD1.5 W8A8 line")
     a = ap.parse_args()
     if a.mode is None:
         a.mode = {"sd35": "w4a16", "sdxl": "w8a8"}.get(a.model, "w8a8-sq")
@@ -411,6 +428,23 @@ def cpu_baseline(threads):
             "per_class": pc, "seconds_per_image": round(r["seconds_per_image"], 1)}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: tensor} -> DIR/<name>.npy in float32, at most DUMP_MAX_BYTES in all
+    (a larger array is cut to a fixed, seeded sample of its elements, in index order)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_MAX_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > budget:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, budget // 4, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def launch_ranks(args):
     """`bench.py --gpus N` run directly (not under torchrun): this parent never touches the GPU;
     it starts N ranks (one process per GPU) through torch.distributed.run on 127.0.0.1 and exits
@@ -491,8 +525,9 @@ def main():
     if rank == 0:
         assert out is not None and torch.isfinite(out.float()).all(), "non-finite latents"
         log(f"timed {args.steps} steps: {dt:.3f}s")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"latents": out})
         int8 = args.mode.endswith("-int8")
-        roof = dominant_kernel_roofline(dev, int8=int8)
         evals_per_s = value * args.denoise_steps  # UNet evals per image per step: 50 steps at CFG batch 2
         path_tflops = evals_per_s * 2 * UNET_GFLOP_PER_SAMPLE / 1e3
         t_min = int8_blended_tmin()
@@ -507,7 +542,6 @@ def main():
                                    f"{args.res}x{args.res}, {B} prompts/GPU "
                                    f"(CFG batch {2 * B}), {args.denoise_steps} DDIM steps, HIP graph per step",
                        "global_batch": B * world, "seq_len": 77, "parallelism": f"dp{world}"},
-            "roofline": roof,
             "path_roofline": {"achieved": round(path_tflops / world, 1), "peak": PEAK_F16_TFLOPS,
                               "unit": "TFLOP/s per GPU", "frac": round(path_tflops / world / PEAK_F16_TFLOPS, 4),
                               "flop_per_image": 2 * args.denoise_steps * UNET_GFLOP_PER_SAMPLE * 1e9},
@@ -520,15 +554,17 @@ def main():
         }
         if args.mode == "w4a16":
             line["weight_stream"] = weight_footprint(model)
-        if not args.no_e2e:
+        if args.full:
+            line["roofline"] = dominant_kernel_roofline(dev, int8=int8)
+        if args.full and not args.no_e2e:
             log("end to end (text encoder + VAE decode) ...")
             line["end_to_end"] = end_to_end(model, out[:B], prompts[:B], dt / args.steps)
-    if world == 1 and not int8 and args.mode.startswith("w8a8") and not args.no_int8_mode:
+    if args.full and world == 1 and not int8 and args.mode.startswith("w8a8") and not args.no_int8_mode:
         # north_star's target mode, measured in the same run: the same SD1.5 W8A8
         # workload quantized with int8_mfma=True, the same steps / warmup protocol
         line["int8_mode"] = int8_mode_line(args, dev, log, lat, full_ctx)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("cpu baseline ...")
             line["cpu_baseline"] = cpu_baseline(args.cpu_threads or None)
         print(json.dumps(line), flush=True)
@@ -739,6 +775,8 @@ def main_sd35(args, model, rank, world, dev, log):
     if rank == 0:
         assert out is not None and torch.isfinite(out.float()).all(), "non-finite latents"
         log(f"timed {args.steps} steps: {dt:.3f}s")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"latents": out})
         gflop = mmdit_gflop_per_sample(cfg, s, sc)
         path_tflops = value * args.denoise_steps * 2 * gflop / 1e3
         line = {
@@ -752,7 +790,6 @@ def main_sd35(args, model, rank, world, dev, log):
                                    f"prompt(s)/GPU (CFG batch {2 * B}), {args.denoise_steps} flow-match Euler "
                                    f"steps, HIP graph per step (SURVEY config C5)",
                        "global_batch": B * world, "seq_len": sc, "parallelism": f"dp{world}"},
-            "roofline": mmdit_dominant_roofline(model, dev, s),
             "path_roofline": {"achieved": round(path_tflops / world, 1), "peak": PEAK_F16_TFLOPS,
                               "unit": "TFLOP/s per GPU", "frac": round(path_tflops / world / PEAK_F16_TFLOPS, 4),
                               "flop_per_image": round(2 * args.denoise_steps * gflop * 1e9)},
@@ -760,7 +797,9 @@ def main_sd35(args, model, rank, world, dev, log):
         }
         if args.mode == "w4a16":
             line["weight_stream"] = weight_footprint(model)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            line["roofline"] = mmdit_dominant_roofline(model, dev, s)
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("cpu baseline ...")
             line["cpu_baseline"] = cpu_baseline_sd35(min(args.cpu_threads or 1 << 30, usable_cores()[0]), cfg, s, sc,
                                                      args.denoise_steps)
@@ -834,6 +873,8 @@ def main_sdxl(args, model, rank, world, dev, log):
     if rank == 0:
         assert out is not None and torch.isfinite(out.float()).all(), "non-finite latents"
         log(f"timed {args.steps} steps: {dt:.3f}s")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"latents": out})
         path_tflops = value * args.denoise_steps * 2 * SDXL_TFLOP_PER_SAMPLE
         line = {
             "metric": f"images/sec SDXL {args.mode.upper()} {args.res}x{args.res} {args.denoise_steps}-step",
@@ -845,12 +886,13 @@ def main_sdxl(args, model, rank, world, dev, log):
                                    f"(CFG batch {2 * B}), {args.denoise_steps} EulerDiscrete steps, HIP graph per step "
                                    f"(SURVEY config C4)",
                        "global_batch": B * world, "seq_len": 77, "parallelism": f"dp{world}"},
-            "roofline": dominant_kernel_roofline(dev, n=2 * B, h=hw, w=hw, c=cfg.block_out_channels[0]),
             "path_roofline": {"achieved": round(path_tflops / world, 1), "peak": PEAK_F16_TFLOPS,
                               "unit": "TFLOP/s per GPU", "frac": round(path_tflops / world / PEAK_F16_TFLOPS, 4),
                               "flop_per_image": round(2 * args.denoise_steps * SDXL_TFLOP_PER_SAMPLE * 1e12)},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            line["roofline"] = dominant_kernel_roofline(dev, n=2 * B, h=hw, w=hw, c=cfg.block_out_channels[0])
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("cpu baseline ...")
             base = cpu_baseline(args.cpu_threads or None)
             # the SD1.5 C1 image's seconds scaled by the FLOP ratio of one SDXL image

@@ -8,7 +8,8 @@ R=${1:-2}; shift
 for i in $(seq 1 "$R"); do
   for side in r05 new; do
     dir=$ROOT; [ "$side" = r05 ] && dir=$ROOT/ab_r05
-    out=$(cd "$dir" && timeout -k 10 500 python3 -u bench.py --no-cpu-baseline --no-e2e "$@" 2>/dev/null | tail -1) || { echo "[ab] $side failed"; exit 1; }
+    full=--full; [ "$side" = r05 ] && full=  # (the round-5 bench.py has no --full: its plain line carries int8_mode)
+    out=$(cd "$dir" && timeout -k 10 500 python3 -u bench.py $full --no-cpu-baseline --no-e2e "$@" 2>/dev/null | tail -1) || { echo "[ab] $side failed"; exit 1; }
     echo "[ab] round $i $side: $(echo "$out" | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); i=d.get("int8_mode") or {}; print(d["value"], d["ms_per_step"], "int8_mode", i.get("value"), i.get("ms_per_step"))')"
   done
 done

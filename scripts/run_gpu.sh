@@ -8,8 +8,9 @@
 #   tests:<pytest args, ',' for spaces>   e.g. tests:tests/test_gpu_small_shapes.py (log: TAG_tests<n>.log)
 #   suite          the full `-m gpu` suite (one process, thread timeouts)
 #   smoke          __graft_entry__.smoke()
-#   bench          the default bench line (fake-quant headline + int8_mode object), 20 steps
-#   bench:<args>   bench.py with extra args (',' for spaces), e.g. bench:--model,sdxl
+#   bench          the plain bench line (the fake-quant headline alone), 20 steps
+#   bench:<args>   bench.py with extra args (',' for spaces), e.g. bench:--model,sdxl; the full line
+#                  (roofline, end_to_end, int8_mode object, cpu_baseline): bench:--full,--steps,20,--warmup,5
 #   prof_fq        rocprofv3 step profile of the fake-quant mode (scripts/prof_bench.sh)
 #   prof_int8      the same for the int8-MFMA mode
 #   py:<script args, ',' for spaces>   a measurement script, 300 s limit (log: TAG_py<n>.log)
